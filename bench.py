@@ -21,7 +21,18 @@ rank answers its own 1M-query batch locally.  --scaling weak: each rank its own
 proteome of the same size (seed + 1000*rank), still one merged index.
 --no-merge: independent shard-local indexes instead.
 
+A plain run sets up, warms up, times the K steps and prints the result line
+(the per-kernel table comes from the warmup builds' events).  --full adds every
+other leg: the mass-window query legs, the cold / end-to-end builds, the CPU
+baseline with its sample parity, the measured copy ceiling, and TrEMBL's plain
+count pass (each still switchable: --queries 0, --no-cold, --no-cpu-baseline);
+without it their keys of the result line are null.
+--dump-outputs DIR writes the index of the last timed build (what a caller of
+the timed path receives) as DIR/<name>.npy, float64: its counts, whole-array
+sums, and a fixed seeded sample of the unique table and the occurrence lists.
+
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--config swissprot|human|1k|semi|trembl]
+                        [--full] [--dump-outputs DIR]
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -100,9 +111,14 @@ def main() -> None:
     ap.add_argument("--config", default="swissprot", choices=sorted(WORKLOADS) + ["trembl"])
     ap.add_argument("--trembl-proteins", type=int, default=50_000_000,
                     help="--config trembl: proteins of the whole synthetic proteome (split over the ranks)")
-    ap.add_argument("--queries", type=int, default=1_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cold", action="store_true", help="skip the cold / end-to-end legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the query, cold / end-to-end, CPU-baseline and copy-ceiling legs "
+                         "(a plain run only warms up and times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's index as DIR/<name>.npy (counts, sums, seeded sample)")
+    ap.add_argument("--queries", type=int, default=1_000_000, help="--full: queries of the query legs (0: skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU-baseline legs")
+    ap.add_argument("--no-cold", action="store_true", help="--full: skip the cold / end-to-end legs")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="engine option (dbi_set_option: tuning switches for experiments), repeatable")
     ap.add_argument("--no-merge", action="store_true",
@@ -310,6 +326,9 @@ def main() -> None:
         n_total_all = float(n_total)
     value = n_total_all / elapsed if elapsed > 0 else 0.0
     ms_per_step = 1000.0 * elapsed / max(args.steps, 1)
+    if args.dump_outputs:
+        # the index of the last timed build, before any later leg builds again
+        dump_index(eng, args.dump_outputs, rank, world)
 
     def kernel_table(acc, builds):
         out = []
@@ -352,7 +371,7 @@ def main() -> None:
 
     # secondary: mass-window queries/sec on the built index (1M queries, +-20 ppm)
     qps = None
-    if args.queries > 0 and merge:
+    if args.full and args.queries > 0 and merge:
         # north_star's all-gatherv: every owner's slice onto every rank, then
         # every rank answers its own 1M batch locally (no exchange per batch)
         if world > 1:
@@ -399,7 +418,7 @@ def main() -> None:
                          f"(dbi_shard_replicate: {rst.n_unique} unique peptides, {rst.n_kept} occurrences)",
                    replicate_ms=1e3 * t_rep,
                    replicate_bytes_per_rank=int(20 * rst.n_unique + 4 * rst.n_kept))
-    if args.queries > 0 and not merge:
+    if args.full and args.queries > 0 and not merge:
         ex = eng.export()["mass"]
         rng = np.random.Generator(np.random.PCG64(7 + rank))
         nq = args.queries
@@ -435,14 +454,14 @@ def main() -> None:
         qps["materialised"] = hits_leg(eng, dm, dt, nq, counts)
 
     cold = None
-    if rank == 0 and world == 1 and not merge and not args.no_cold:
+    if args.full and rank == 0 and world == 1 and not merge and not args.no_cold:
         # the reference's real use is a one-off build (DBIndexer.run): the cold
         # pipeline (no capacities, grids, map or graph from earlier builds),
         # and FASTA file -> index end to end
         cold = cold_legs(eng, prm, pp, d_res, d_off, dev, args.config, options)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # reference-semantics CPU restatement (oracle/cpu_ref.cpp) on a bounded
         # sample of the same workload: one thread per host core (protein ranges,
         # then row ranges) and single-threaded like the reference
@@ -457,7 +476,7 @@ def main() -> None:
     prof, prof_src = pmc_summary()
     dom_prof = (prof or {}).get("stages", {}).get(dom["kernel"], {}) if dom else {}
     build_traffic = ((prof or {}).get("build") or {}).get("traffic_bytes") if not merge else None
-    copy_gbps = hbm_copy_gbps(dev) if rank == 0 else None
+    copy_gbps = hbm_copy_gbps(dev) if args.full and rank == 0 else None
     build_gbps = build_alg / (ms_per_step * 1e-3) / 1e9
     if rank == 0:
         out = {
@@ -544,6 +563,37 @@ def main() -> None:
     eng.close()
     if coord is not None:
         coord.close()
+
+
+DUMP_ROWS = 1 << 19  # sampled rows per table: 9 float64 arrays of it, 36 MiB in all
+
+
+def dump_index(eng, dirpath: str, rank: int, world: int) -> None:
+    """--dump-outputs: the engine's current index (dbi_export: the mass-sorted
+    unique table + the occurrence CSR; at N>1 this rank's owner slice) as
+    float64 .npy files (integers below 2^53 stay exact): counts (n_total, n_dropped,
+    n_kept, n_unique, n_keys), sums (every exported array summed whole), and a
+    fixed seeded sample of DUMP_ROWS / N unique rows (rows, mass, prot_id,
+    offset, length, occ_begin, occ_end) and occurrences (occ_rows, occ_prot);
+    tables no larger than the sample are written whole."""
+    st = eng.stats()
+    ex = eng.export()
+    U, K = ex["mass"].shape[0], ex["occ_prot"].shape[0]
+    n = max(DUMP_ROWS // max(world, 1), 1)
+    rng = np.random.Generator(np.random.PCG64(11))
+    rows = np.sort(rng.integers(0, U, n)) if U > n else np.arange(U)
+    occ = np.sort(rng.integers(0, K, n)) if K > n else np.arange(K)
+    out = dict(counts=np.array([st.n_total, st.n_dropped, st.n_kept, st.n_unique, st.n_keys]),
+               sums=np.array([float(ex["mass"].sum())] +
+                             [float(ex[k].sum(dtype=np.uint64)) for k in ("prot_id", "offset", "length", "occ_off",
+                                                                           "occ_prot")]),
+               rows=rows, mass=ex["mass"][rows], prot_id=ex["prot_id"][rows], offset=ex["offset"][rows],
+               length=ex["length"][rows], occ_begin=ex["occ_off"][rows], occ_end=ex["occ_off"][rows + 1],
+               occ_rows=occ, occ_prot=ex["occ_prot"][occ])
+    os.makedirs(dirpath, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, f"{name}{sfx}.npy"), np.asarray(a, dtype=np.float64))
 
 
 def chunk_family(kernels, n_total):
@@ -863,23 +913,33 @@ def run_trembl(args, world: int, rank: int, dev: int, coord, options=None) -> No
     hist = (d_hist_all if comm is not None else d_hist).download(np.uint64, nb + 1)
     if int(hist.sum()) * args.steps != int(n_all):
         raise RuntimeError(f"bucket counts {int(hist.sum())} do not add up to totalSeqCount {int(n_all) // args.steps}")
-    # beside it: the plain count (totalSeqCount only, dbi_count), timed on its own
-    if world > 1:
-        coord.barrier()
-    synchronize(dev)
-    t_c = time.perf_counter()
-    n_c = count_only()
-    synchronize(dev)
-    if world > 1:
-        coord.barrier()
-    t_c = time.perf_counter() - t_c
-    if world > 1:
-        t_c = coord.allreduce([t_c], "max")[0]
-        n_c = coord.allreduce([float(n_c)], "sum")[0]
-    if int(n_c) != int(n_all) // args.steps:
-        raise RuntimeError(f"dbi_count {int(n_c)} != the bucket pass's totalSeqCount {int(n_all) // args.steps}")
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = f"_rank{rank}" if world > 1 else ""
+        np.save(os.path.join(args.dump_outputs, f"bucket_counts{sfx}.npy"), hist.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, f"total_seq_count{sfx}.npy"), np.array([float(n_step)]))
+    # beside it (--full): the plain count (totalSeqCount only, dbi_count), timed on its own
+    count_leg = None
+    if args.full:
+        if world > 1:
+            coord.barrier()
+        synchronize(dev)
+        t_c = time.perf_counter()
+        n_c = count_only()
+        synchronize(dev)
+        if world > 1:
+            coord.barrier()
+        t_c = time.perf_counter() - t_c
+        if world > 1:
+            t_c = coord.allreduce([t_c], "max")[0]
+            n_c = coord.allreduce([float(n_c)], "sum")[0]
+        if int(n_c) != int(n_all) // args.steps:
+            raise RuntimeError(f"dbi_count {int(n_c)} != the bucket pass's totalSeqCount {int(n_all) // args.steps}")
+        count_leg = {"ms": 1e3 * t_c, "peptides_per_s": n_c / t_c,
+                     "kind": "dbi_count (totalSeqCount only, no buckets) over every chunk, one pass after "
+                             "the timed steps"}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import cref
         sample = fasta.synth_proteome(seed, 0, 120000, 0, tables)  # ~10 s of single-core count
         cp = prm.to_c()
@@ -929,9 +989,7 @@ def run_trembl(args, world: int, rank: int, dev: int, coord, options=None) -> No
                               "combined": "ncclAllReduce (dbi_comm_allreduce_u64)" if world > 1 else "one rank",
                               "kind": "the timed step: dbi_count_buckets over every chunk + the allreduce; the "
                                       "last entry is past the last bucket"},
-            "count_only": {"ms": 1e3 * t_c, "peptides_per_s": n_c / t_c,
-                           "kind": "dbi_count (totalSeqCount only, no buckets) over every chunk, one pass after "
-                                   "the timed steps"},
+            "count_only": count_leg,
             "roofline": {"bound": "hbm", "kernel": "digest_count",
                          "achieved": alg / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": alg / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, "traffic": None,
