@@ -1387,6 +1387,10 @@ int upload_residues(dbi_handle* h, const uint8_t* residues, uint64_t n_res, bool
 int upload_inputs(dbi_handle* h, const uint8_t* residues, uint64_t n_res, const uint64_t* prot_off, uint64_t n_prot,
                   bool* ptm) {
     int rc;
+    // res / poff are about to be overwritten or freed: nothing built over them
+    // answers any more, and dbi_rebuild has nothing to digest until they are whole
+    h->built = false;
+    h->inputs_resident = false;
     DBI_HIP(hipSetDevice(h->device));
     if ((rc = h->res.ensure(n_res + 16))) return rc;
     if ((rc = h->poff.ensure(n_prot + 1))) return rc;
@@ -1607,6 +1611,9 @@ int dbi_build(dbi_handle* h, const uint8_t* residues, uint64_t n_res, const uint
     bool ptm = false;  // the upload looks for '[' as it copies
     if ((rc = upload_inputs(h, residues, n_res, prot_off, n_prot, &ptm))) return rc;
     if (ptm) {  // inline '[formula]' PTMs
+        // the text just uploaded holds formulas nobody has validated: not an input
+        // of dbi_rebuild until build_with_ptms has planned it and uploaded it again
+        h->inputs_resident = false;
         if ((rc = build_with_ptms(h, residues, n_res, prot_off, n_prot))) return rc;
         return finish_build(h);
     }

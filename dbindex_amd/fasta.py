@@ -260,6 +260,7 @@ def _from_native(call, with_defs: bool) -> PackedProteins:
         buf = (ctypes.c_uint8 * R).from_address(f.residues)
         buf._owner = owner  # the memoryview under the array keeps buf, buf keeps the result
         res = np.ctypeslib.as_array(buf)
+        res.flags.writeable = False  # the library's buffer, shared by every view of it
     else:
         res = np.zeros(0, np.uint8)
     offs = np.ctypeslib.as_array(f.offsets, shape=(P + 1,)).astype(np.uint64)

@@ -259,6 +259,28 @@ def test_native_fasta_read_file(tmp_path):
         fasta.read_fasta(str(tmp_path / "missing.fasta"))
 
 
+def test_native_fasta_residue_view_is_read_only(tmp_path):
+    """read_fasta / parse_fasta hand out a zero-copy view of the library's
+    buffer: writing through it (or through a slice of it) raises; a copy, as
+    PackedProteins.slice makes, is writable."""
+    pp = fasta.config("1k").slice(0, 20)
+    path = tmp_path / "p.fasta"
+    with open(path, "w") as fh:
+        fasta.write_fasta(pp, fh)
+    with open(path) as fh:
+        text = fh.read()
+    for back in (fasta.read_fasta(str(path)), fasta.parse_fasta(text)):
+        assert not back.residues.flags.writeable
+        with pytest.raises(ValueError, match="read-only"):
+            back.residues[0] = ord("A")
+        with pytest.raises(ValueError, match="read-only"):
+            back.residues[5:9][:] = 0
+        assert np.array_equal(back.residues, pp.residues)
+        part = back.slice(0, 3)
+        part.residues[0] = ord("A")  # a copy of its own
+        assert back.residues[0] == pp.residues[0]
+
+
 def test_index_file_matches_header(tmp_path):
     """dbi_index_file_matches (host only): missing / foreign files never match."""
     p = DBIndexSearchParams.trypsin(2).to_c()

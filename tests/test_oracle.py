@@ -224,6 +224,88 @@ def test_twin_tag_collisions():
     assert any(keys[i] == keys[i + 1] for i in range(len(keys) - 1))
 
 
+def _twins_agree(prm, seqs):
+    """cref and pyref bit-exact on one proteome: the digest, the counts and
+    every index array (mass bits, representative, occurrence lists, keys)."""
+    pp = fasta.PackedProteins.from_sequences(seqs)
+    cp = prm.to_c()
+    d = cref.digest(cp, pp.residues, pp.offsets)
+    py = pyref.digest(prm, seqs)
+    assert len(py) == d.mass.shape[0]
+    assert np.array_equal(np.array([x[0] for x in py], np.float64).view(np.uint64), d.mass.view(np.uint64))
+    assert [x[1:4] for x in py] == list(zip(d.pid.tolist(), d.offset.tolist(), d.length.tolist()))
+    assert [bool(x[4]) for x in py] == [bool(v) for v in d.dropped]
+    ix = cref.Index(cp, pp.residues, pp.offsets)
+    st = pyref.build(prm, seqs)
+    u = ix.unique()
+    assert len(st.flat) == ix.n_unique and st.total_seq_count == ix.n_total == len(py)
+    assert np.array_equal(np.array([g[0] for g in st.flat], np.float64).view(np.uint64), u["mass"].view(np.uint64))
+    assert [(g[3][0], g[1], g[2]) for g in st.flat] == \
+        list(zip(u["prot_id"].tolist(), u["offset"].tolist(), u["length"].tolist()))
+    assert [p for g in st.flat for p in g[3]] == u["occ_prot"].tolist()
+    assert np.array_equal(np.cumsum([0] + [len(g[3]) for g in st.flat]), u["occ_off"].astype(np.int64))
+    assert st.number_sequences() == ix.n_keys and st.entry_keys() == list(ix.entry_keys())
+    total, dropped = cref.count(cp, pp.residues, pp.offsets)
+    assert total == len(py) and dropped == sum(1 for x in py if x[4]) == ix.n_dropped
+    hist = cref.count_buckets(cp, pp.residues, pp.offsets)
+    nb = prm.index_factor
+    want = np.zeros(nb + 1, np.uint64)
+    for occ in py:
+        want[min(pyref.java_int(occ[0]) // (8000 // nb), nb)] += 1
+    assert np.array_equal(hist, want)
+    return ix
+
+
+@pytest.mark.parametrize("name,prm", [
+    ("tryp2_nocutP", DBIndexSearchParams.trypsin(2, enzyme_nocut_residues="P")),
+    ("tryp3", DBIndexSearchParams.trypsin(3)),
+    ("semi1", DBIndexSearchParams.semi_tryptic(1)),
+    ("nonspec30", DBIndexSearchParams.non_specific(30)),
+    ("mand_K", DBIndexSearchParams.trypsin(2, mandatory_internal_aas="K")),
+])
+def test_twins_on_seam_proteome(name, prm):
+    """The seam proteome of tests/test_seams_gpu.py, reduced to a dozen
+    shifts: a new shape for the oracle too (a letter heavier than maxMH, the
+    probe's KP / RP, KR, RR, short peptide and C-terminal tail)."""
+    from tests import helpers as H
+    shifts = [-77, -66, -64, -33, -17, -16, -15, -8, -1, 0, 1, 2]
+    seqs, starts = H.seam_proteome(shifts, tail=60)
+    assert [s - 4096 * (2 * i + 1) for i, s in enumerate(starts)] == shifts
+    ix = _twins_agree(H.seam_params(prm), seqs)
+    assert ix.n_total > 200
+
+
+@pytest.mark.parametrize("name,prm", [
+    ("tryp2", DBIndexSearchParams.trypsin(2, max_precursor_mass=20000.0)),
+    ("tryp0", DBIndexSearchParams.trypsin(0, max_precursor_mass=20000.0)),
+    ("semi2", DBIndexSearchParams.semi_tryptic(2, max_precursor_mass=20000.0)),
+])
+def test_twins_on_horizon_probes(name, prm):
+    """Glycine runs of 126..130 positions to the next stop / the last
+    candidate end under a 20000-Da maxMH (the GPU walk's 128-position
+    horizon): peptides of up to 140 residues, in both restatements."""
+    from tests import helpers as H
+    seqs = [p for _, _, p in H.horizon_proteins()]
+    ix = _twins_agree(H.seam_params(prm), seqs)
+    assert int(ix.unique()["length"].max()) >= 131
+
+
+@pytest.mark.parametrize("mc", [0, 2])
+def test_twins_on_many_string_family(mc):
+    """70 different strings in one equal-(mass, tag) group, copies in a
+    shuffled order: unique order by first appearance, in both restatements."""
+    from tests import helpers as H
+    fam = H.perm_family()
+    assert len(fam) >= 70
+    seqs = H.UNRELATED[:5] + H.family_proteins(70, 350, seed=1) + H.UNRELATED[5:10]
+    ix = _twins_agree(DBIndexSearchParams.trypsin(mc), seqs)
+    u = ix.unique()
+    grp = [seqs[int(p)][int(o):int(o) + int(l)] for p, o, l in zip(u["prot_id"], u["offset"], u["length"])
+           if l == 13 and seqs[int(p)].startswith("ACDE")]
+    seen = list(dict.fromkeys(s for s in seqs if s.startswith("ACDE")))
+    assert grp == seen and len(grp) == 70
+
+
 # ---------------------------------------------------------------- golden
 @pytest.mark.parametrize("fname,prm,nprot", [
     ("golden_1k_tryp0.npz", DBIndexSearchParams.trypsin(0), 1000),
