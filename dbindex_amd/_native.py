@@ -10,7 +10,7 @@ import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
-from .params import DbiParams
+from .params import DbiParams, DbiPeptideFilter
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DBI_LIB_PATH") or os.path.join(HERE, "libdbindex_hip.so")  # override: experiments
@@ -121,6 +121,8 @@ SIGNATURES = [
     ("dbi_set_bucket_drop", c_int, [P, c_int]),
     ("dbi_set_windows", c_int, [P, P, P, c_uint64, c_int]),
     ("dbi_rebuild", c_int, [P]),
+    ("dbi_set_peptide_filter", c_int, [P, POINTER(DbiPeptideFilter)]),
+    ("dbi_peptide_filter_is_valid", c_int, [POINTER(DbiPeptideFilter), c_char_p, c_uint64, POINTER(c_int)]),
     ("dbi_stage_times", c_int, [P, P, P, P, c_uint64, POINTER(c_uint64)]),
     ("dbi_shard_digest", c_int, [P, P, c_uint64, P, c_uint64, c_uint64, c_uint64, c_int, c_int]),
     ("dbi_shard_samples", c_int, [P, P]),
@@ -173,6 +175,9 @@ SIGNATURES = [
     ("dbi_index_save", c_int, [P, c_char_p]),
     ("dbi_index_load", c_int, [P, c_char_p]),
     ("dbi_index_file_matches", c_int, [POINTER(DbiParams), c_char_p, POINTER(c_int)]),
+    ("dbi_index_file_matches_filtered", c_int, [POINTER(DbiParams), POINTER(DbiPeptideFilter), c_char_p,
+                                                POINTER(c_int)]),
+    ("dbi_store_set_peptide_filter", c_int, [P, POINTER(DbiPeptideFilter)]),
     ("dbi_store_set_persist", c_int, [P, c_int]),
     ("dbi_store_set_unindexed", c_int, [P, c_int]),
     ("dbi_fasta_parse", c_int, [P, c_uint64, c_int, POINTER(POINTER(DbiFasta))]),

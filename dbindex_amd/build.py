@@ -18,7 +18,7 @@ LIB = os.path.join(HERE, "libdbindex_hip.so")
 # the test-hook variant (options test_fail / test_split_skew): tests only
 LIB_HOOKS = os.path.join(HERE, "libdbindex_hip_hooks.so")
 HOOK_SOURCES = ("dbi_engine.hip", "dbi_shard.hip")
-SOURCES = ["dbi_device.hip", "dbi_engine.hip", "dbi_shard.hip", "dbi_stream.hip", "dbi_persist.hip", "dbi_store.cpp", "dbi_fasta.cpp"]
+SOURCES = ["dbi_device.hip", "dbi_engine.hip", "dbi_shard.hip", "dbi_stream.hip", "dbi_persist.hip", "dbi_store.cpp", "dbi_fasta.cpp", "dbi_filter.cpp"]
 ARCH = os.environ.get("DBI_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
          "-Wno-unused-result", "-Wshadow", f"--offload-arch={ARCH}"]

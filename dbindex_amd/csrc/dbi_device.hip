@@ -283,6 +283,87 @@ hipError_t launch_tile_proteins(const uint32_t* d_poff, uint32_t n_prot, uint32_
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Motif pre-pass of a sequence peptide filter (PeptideFilterBySequence:
+// Matcher.find over every prefix of every walk, DBIndexer.java:309-313).
+// fend[e] = length of the shortest alternative matching the residues that end
+// at e, inside e's own protein; 0: none.  A walk from s is invalid from the
+// first e with a match [b, e], b >= s; the shortest alternative ending at e
+// has the latest b, so that test is fend[e] <= e - s + 1, exact per start.
+// One tile of FE_TILE ends per block: its residues with a halo of
+// PF_MAX_ATOMS - 1 before them, the protein starts inside as a bit map, and
+// the class masks, all in LDS (8.6 KiB a block).
+// ---------------------------------------------------------------------------
+constexpr uint32_t FE_TILE = 4096;
+constexpr uint32_t FE_THREADS = 256;
+constexpr uint32_t FE_HALO = PF_MAX_ATOMS - 1;
+constexpr uint32_t FE_WORDS = (FE_TILE + FE_HALO) / 64 + 2;
+
+struct FendSmem {
+    uint32_t mask[PF_MAX_ALTS * PF_MAX_ATOMS * 8];  // [alt][position][word]
+    uint32_t len[PF_MAX_ALTS];
+    uint32_t n_alt;
+    unsigned long long stm[FE_WORDS];  // bit i: a protein starts at window position i
+    uint8_t res[FE_TILE + FE_HALO + 1];
+};
+
+__global__ void __launch_bounds__(FE_THREADS)
+k_filter_ends(const PepFilterProg* __restrict__ prog, const uint8_t* __restrict__ res,
+              const uint32_t* __restrict__ poff, uint32_t n_prot, uint32_t n_res, uint8_t* __restrict__ fend) {
+    __shared__ FendSmem sm;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t t0 = blockIdx.x * FE_TILE;
+    const uint32_t t_end = min(t0 + FE_TILE, n_res);
+    const uint32_t w0 = t0 >= FE_HALO ? t0 - FE_HALO : 0u;
+    const uint32_t nb = t_end - w0;  // <= FE_TILE + FE_HALO
+    const uint32_t* __restrict__ pm = &prog->mask[0][0][0];
+    for (uint32_t i = tid; i < (uint32_t)(PF_MAX_ALTS * PF_MAX_ATOMS * 8); i += FE_THREADS) sm.mask[i] = pm[i];
+    if (tid < (uint32_t)PF_MAX_ALTS) sm.len[tid] = prog->len[tid];
+    if (tid == 0) sm.n_alt = min(prog->n_alt, (uint32_t)PF_MAX_ALTS);
+    for (uint32_t i = tid; i < nb; i += FE_THREADS) sm.res[i] = res[w0 + i];
+    for (uint32_t i = tid; i < FE_WORDS; i += FE_THREADS) sm.stm[i] = 0ull;
+    __syncthreads();
+    // protein starts in [w0, t_end): pf = the protein holding w0 (poff[0] = 0 <= w0)
+    const uint32_t pf = find_le(poff, 0, n_prot, w0);
+    if (tid == 0 && poff[pf] == w0) atomicOr(&sm.stm[0], 1ull);
+    for (uint32_t p = pf + 1 + tid; p < n_prot; p += FE_THREADS) {
+        const uint32_t o = poff[p];
+        if (o >= t_end) break;
+        if (o < w0) continue;  // (offsets not ascending: device input nobody validated)
+        atomicOr(&sm.stm[(o - w0) >> 6], 1ull << ((o - w0) & 63));
+    }
+    __syncthreads();
+    const uint32_t n_alt = sm.n_alt;
+    for (uint32_t i = t0 - w0 + tid; i < nb; i += FE_THREADS) {
+        // residues available back to the start of this end's protein (16: more than any alternative)
+        const uint32_t lo = i >= FE_HALO ? i - FE_HALO : 0u;
+        const uint32_t w = lo >> 6, b = lo & 63u;
+        unsigned long long v = b ? (sm.stm[w] >> b) | (sm.stm[w + 1] << (64 - b)) : sm.stm[w];
+        v &= (2ull << (i - lo)) - 1ull;  // window positions lo .. i
+        const uint32_t avail = v ? i - (lo + 63u - (uint32_t)__clzll((long long)v)) + 1u : (uint32_t)PF_MAX_ATOMS;
+        uint32_t best = 0;
+        for (uint32_t a = 0; a < n_alt; ++a) {
+            const uint32_t L = sm.len[a];
+            if (L == 0 || L > avail || L > i + 1 || (best && L >= best)) continue;
+            bool ok = true;
+            for (uint32_t k = 0; k < L && ok; ++k) {
+                const uint32_t c = sm.res[i + 1 - L + k];
+                ok = (sm.mask[(a * PF_MAX_ATOMS + k) * 8 + (c >> 5)] >> (c & 31u)) & 1u;
+            }
+            if (ok) best = L;
+        }
+        fend[w0 + i] = (uint8_t)best;
+    }
+}
+
+hipError_t launch_filter_ends(const PepFilterProg* d_prog, const uint8_t* d_res, const uint32_t* d_poff,
+                              uint32_t n_prot, uint32_t n_res, uint8_t* d_fend, hipStream_t s) {
+    if (n_res == 0 || n_prot == 0) return hipSuccess;
+    DBI_LAUNCH(k_filter_ends, dim3((n_res + FE_TILE - 1) / FE_TILE), dim3(FE_THREADS), 0, s, d_prog, d_res, d_poff,
+               n_prot, n_res, d_fend);
+    return hipGetLastError();
+}
+
 struct WalkOut {
     uint32_t kept;
     uint32_t dropped;
@@ -320,7 +401,20 @@ __device__ __forceinline__ void hist_add(const DevParams& dp, uint32_t* hist, do
     atomicAdd(&hist[min(java_d2i(m) / dp.br, dp.nb)], 1u);
 }
 
-template <bool EMIT, bool SEMI, bool MAND, bool HIST = false>
+// FILT: a peptide filter (dbi_set_peptide_filter) ends the walk at the first
+// end whose peptide is invalid, asked first in a step (DBIndexer.java:309-313);
+// fend is read from HBM (L2: a byte per residue, shared by the tile's walks).
+__device__ __forceinline__ bool filter_breaks(const DevParams& dp, uint32_t fl, uint32_t s, uint32_t e,
+                                              uint32_t& focc) {
+    if (dp.pf_kind == 1) {
+        focc += (fl / F_FOCC) & 1u;
+        return focc > (uint32_t)dp.pf_max;
+    }
+    const uint32_t fe = dp.fend[e];
+    return fe != 0 && fe <= e - s + 1;
+}
+
+template <bool EMIT, bool SEMI, bool MAND, bool HIST = false, bool FILT = false>
 __device__ __forceinline__ WalkOut walk_lds(const DevParams& dp, const DigestSmem& sm, uint32_t w0, uint32_t wlim,
                                             uint32_t s, bool n_ok, uint64_t loc, Rec* __restrict__ out,
                                             const Rec* out_end, uint32_t* hist = nullptr) {
@@ -340,12 +434,17 @@ __device__ __forceinline__ WalkOut walk_lds(const DevParams& dp, const DigestSme
     uint32_t e = s;
     uint32_t cur = sm.win[e - w0];
     bool ovf;
+    uint32_t focc = 0;  // FILT: counted residues in [s, e]
     // single exit at the bottom: the window overflow is one more predicate
     for (;;) {
         // next window entry first: its LDS latency overlaps this step
         const uint32_t nxt = sm.win[min(e + 1, wlim - 1) - w0];
         const uint32_t c = cur & 0xFFu;
         const uint32_t fl = cur >> 8;
+        if (FILT && filter_breaks(dp, fl, s, e, focc)) {      // :309-313
+            ovf = false;
+            break;
+        }
         m = m + sm.mass[c];                                   // :306-308
         mc += (int)(fl & F_CLEAVE);                           // :314-316
         if (EMIT) tail = (tail << 8) | c;
@@ -401,23 +500,23 @@ struct RecSink {  // 16-B records at out[k] (below out_end)
 // The same loop reading residues from HBM (walks that run past the staged
 // window, e.g. through zero-mass residues): flags from the residue tables,
 // the cut from the next residue and the protein end pe.
-template <bool EMIT, bool SEMI, bool MAND, bool HIST = false, typename Sink = RecSink>
+template <bool EMIT, bool SEMI, bool MAND, bool HIST = false, typename Sink = RecSink, bool FILT = false>
 __device__ WalkOut walk_global_to(const DevParams& dp, const double* __restrict__ s_mass,
                                   const uint8_t* __restrict__ s_flags, const uint8_t* __restrict__ g_res,
                                   uint32_t s, uint32_t pe, bool n_ok, const Sink& sink, uint32_t* hist = nullptr,
                                   uint32_t hist_from = 0);
 
-template <bool EMIT, bool SEMI, bool MAND, bool HIST = false>
+template <bool EMIT, bool SEMI, bool MAND, bool HIST = false, bool FILT = false>
 __device__ __forceinline__ WalkOut walk_global(const DevParams& dp, const double* __restrict__ s_mass,
                                                const uint8_t* __restrict__ s_flags, const uint8_t* __restrict__ g_res,
                                                uint32_t s, uint32_t pe, bool n_ok, uint64_t loc,
                                                Rec* __restrict__ out, const Rec* out_end, uint32_t* hist = nullptr,
                                                uint32_t hist_from = 0) {
-    return walk_global_to<EMIT, SEMI, MAND, HIST>(dp, s_mass, s_flags, g_res, s, pe, n_ok, RecSink{out, out_end, loc},
-                                                  hist, hist_from);
+    return walk_global_to<EMIT, SEMI, MAND, HIST, RecSink, FILT>(dp, s_mass, s_flags, g_res, s, pe, n_ok,
+                                                                 RecSink{out, out_end, loc}, hist, hist_from);
 }
 
-template <bool EMIT, bool SEMI, bool MAND, bool HIST, typename Sink>
+template <bool EMIT, bool SEMI, bool MAND, bool HIST, typename Sink, bool FILT>
 __device__ WalkOut walk_global_to(const DevParams& dp, const double* __restrict__ s_mass,
                                   const uint8_t* __restrict__ s_flags, const uint8_t* __restrict__ g_res,
                                   uint32_t s, uint32_t pe, bool n_ok, const Sink& sink, uint32_t* hist,
@@ -431,9 +530,11 @@ __device__ WalkOut walk_global_to(const DevParams& dp, const double* __restrict_
     if (EMIT)
         for (uint32_t k = 0; k < 4 && s + k < pe; ++k) head |= (uint32_t)g_res[s + k] << (8 * k);
     uint32_t kept = 0, dropped = 0;
+    uint32_t focc = 0;
     for (uint32_t e = s; e < pe; ++e) {
         const uint32_t c = g_res[e];
         const uint32_t fl = s_flags[c];
+        if (FILT && filter_breaks(dp, fl, s, e, focc)) break;
         m = m + s_mass[c];
         mc += (int)(fl & F_CLEAVE);
         if (EMIT) tail = (tail << 8) | c;
@@ -667,7 +768,7 @@ __device__ __forceinline__ uint32_t tile_protein(const DigestSmem& sm, const Til
 }
 
 // One candidate: LDS walk, or the HBM walk when it outruns the window
-template <bool EMIT, bool SEMI, bool MAND, bool HIST = false>
+template <bool EMIT, bool SEMI, bool MAND, bool HIST = false, bool FILT = false>
 __device__ __forceinline__ WalkOut walk_candidate(const DevParams& dp, const DigestSmem& sm, const TileCtx& tc,
                                                   const uint8_t* __restrict__ d_res,
                                                   const uint32_t* __restrict__ d_poff, uint32_t j,
@@ -681,11 +782,11 @@ __device__ __forceinline__ WalkOut walk_candidate(const DevParams& dp, const Dig
         const uint32_t p = tile_protein(sm, tc, d_poff, s, pstart);
         loc = rec_loc(p, s - pstart, tc.w);
     }
-    WalkOut w = walk_lds<EMIT, SEMI, MAND, HIST>(dp, sm, tc.w0, tc.w_end, s, n_ok, loc, o, o_end, hist);
+    WalkOut w = walk_lds<EMIT, SEMI, MAND, HIST, FILT>(dp, sm, tc.w0, tc.w_end, s, n_ok, loc, o, o_end, hist);
     if (w.overflow) {  // (HIST: the LDS walk counted the ends before w_end - 1, the same as the HBM walk's)
         const uint32_t pe = d_poff[find_le(d_poff, tc.pf, tc.pl + 1, s) + 1];
-        w = walk_global<EMIT, SEMI, MAND, HIST>(dp, sm.mass, sm.flags, d_res, s, pe, n_ok, loc, o, o_end, hist,
-                                                tc.w_end - 1);
+        w = walk_global<EMIT, SEMI, MAND, HIST, FILT>(dp, sm.mass, sm.flags, d_res, s, pe, n_ok, loc, o, o_end, hist,
+                                                      tc.w_end - 1);
     }
     return w;
 }
@@ -724,7 +825,7 @@ __device__ __forceinline__ void hist_flush(const DevParams& dp, const uint32_t* 
         if (s_hist[b]) atomicAdd(&d_hist[b], (unsigned long long)s_hist[b]);
 }
 
-template <bool EMIT, bool SEMI, bool MAND, bool HIST = false>
+template <bool EMIT, bool SEMI, bool MAND, bool HIST = false, bool FILT = false>
 __global__ void __launch_bounds__(DIGEST_THREADS)
 k_digest(DevParams dp, const double* __restrict__ d_mass_tab, const uint8_t* __restrict__ d_flags,
          const uint8_t* __restrict__ d_res, const uint32_t* __restrict__ d_poff, uint32_t n_prot,
@@ -743,8 +844,8 @@ k_digest(DevParams dp, const double* __restrict__ d_mass_tab, const uint8_t* __r
     if (!EMIT) {
         uint32_t kept = 0, dropped = 0;
         for (uint32_t j = jb; j < je; ++j) {
-            const WalkOut w = walk_candidate<false, SEMI, MAND, HIST>(dp, sm, tc, d_res, d_poff, j, nullptr, nullptr,
-                                                                      s_hist);
+            const WalkOut w = walk_candidate<false, SEMI, MAND, HIST, FILT>(dp, sm, tc, d_res, d_poff, j, nullptr,
+                                                                            nullptr, s_hist);
             kept += w.kept;
             dropped += w.dropped;
         }
@@ -759,7 +860,7 @@ k_digest(DevParams dp, const double* __restrict__ d_mass_tab, const uint8_t* __r
     Rec* out = d_out + d_blk[blockIdx.x] + block_excl_scan<DIGEST_THREADS, uint32_t>(my, sm.tmp, tot);
     const Rec* out_end = reinterpret_cast<const Rec*>(~(uintptr_t)0 & ~(uintptr_t)15);  // sized from the count pass
     for (uint32_t j = jb; j < je; ++j)
-        out += walk_candidate<true, SEMI, MAND>(dp, sm, tc, d_res, d_poff, j, out, out_end).kept;
+        out += walk_candidate<true, SEMI, MAND, false, FILT>(dp, sm, tc, d_res, d_poff, j, out, out_end).kept;
 }
 
 
@@ -1283,7 +1384,7 @@ __device__ unsigned long long tile_lookback(unsigned long long* __restrict__ sta
     return tile_lookback_wait(status, tile, epoch, total);
 }
 
-template <bool SEMI, bool MAND>
+template <bool SEMI, bool MAND, bool FILT = false>
 __global__ void __launch_bounds__(DIGEST_THREADS)
 k_digest_fused(DevParams dp, const double* __restrict__ d_mass_tab, const uint8_t* __restrict__ d_flags,
                const uint8_t* __restrict__ d_res, const uint32_t* __restrict__ d_poff, uint32_t n_prot,
@@ -1304,7 +1405,7 @@ k_digest_fused(DevParams dp, const double* __restrict__ d_mass_tab, const uint8_
     // occupancy, and its emit walk is issue-bound)
     uint32_t kept = 0, dropped = 0;
     for (uint32_t j = jb; j < je; ++j) {
-        const WalkOut w = walk_candidate<false, SEMI, MAND>(dp, sm, tc, d_res, d_poff, j, nullptr, nullptr);
+        const WalkOut w = walk_candidate<false, SEMI, MAND, false, FILT>(dp, sm, tc, d_res, d_poff, j, nullptr, nullptr);
         kept += w.kept;
         dropped += w.dropped;
     }
@@ -1326,7 +1427,7 @@ k_digest_fused(DevParams dp, const double* __restrict__ d_mass_tab, const uint8_
     Rec* out = d_out + base;
     const Rec* out_end = d_out + cap;
     for (uint32_t j = jb; j < je; ++j)
-        out += walk_candidate<true, SEMI, MAND>(dp, sm, tc, d_res, d_poff, j, out, out_end).kept;
+        out += walk_candidate<true, SEMI, MAND, false, FILT>(dp, sm, tc, d_res, d_poff, j, out, out_end).kept;
 }
 
 hipError_t launch_digest_fused(const DevParams& dp, const double* d_mass_tab, const uint8_t* d_flags,
@@ -1335,9 +1436,16 @@ hipError_t launch_digest_fused(const DevParams& dp, const double* d_mass_tab, co
                                Rec* d_out, uint32_t cap, Counters* d_ctr, hipStream_t s) {
     const uint32_t nblk = (n_res + DIGEST_TILE - 1) / DIGEST_TILE;
     if (nblk == 0) return hipSuccess;
-#define DBI_FUSED(SEMI, MAND)                                                                              \
-    DBI_LAUNCH((k_digest_fused<SEMI, MAND>), dim3(nblk), dim3(DIGEST_THREADS), 0, s, dp, d_mass_tab, d_flags, \
-               d_res, d_poff, n_prot, n_res, d_tile_pf, d_status, epoch, d_out, cap, d_ctr)
+#define DBI_FUSED(SEMI, MAND)                                                                                 \
+    do {                                                                                                      \
+        if (dp.pf_kind)                                                                                       \
+            DBI_LAUNCH((k_digest_fused<SEMI, MAND, true>), dim3(nblk), dim3(DIGEST_THREADS), 0, s, dp,        \
+                       d_mass_tab, d_flags, d_res, d_poff, n_prot, n_res, d_tile_pf, d_status, epoch, d_out,  \
+                       cap, d_ctr);                                                                           \
+        else                                                                                                  \
+            DBI_LAUNCH((k_digest_fused<SEMI, MAND>), dim3(nblk), dim3(DIGEST_THREADS), 0, s, dp, d_mass_tab,  \
+                       d_flags, d_res, d_poff, n_prot, n_res, d_tile_pf, d_status, epoch, d_out, cap, d_ctr); \
+    } while (0)
     if (dp.semi) {
         if (dp.mand_mode) DBI_FUSED(true, true); else DBI_FUSED(true, false);
     } else {
@@ -2433,10 +2541,18 @@ static hipError_t launch_digest(const DevParams& dp, const double* d_mass_tab, c
     const uint32_t nblk = (n_res + DIGEST_TILE - 1) / DIGEST_TILE;
     if (nblk == 0) return hipSuccess;
     static_assert(!EMIT || !HIST, "bucket counts come from COUNT passes");
-#define DBI_DIGEST(SEMI, MAND)                                                                              \
-    DBI_LAUNCH((k_digest<EMIT, SEMI, MAND, HIST>), dim3(nblk), dim3(DIGEST_THREADS), 0, s, dp, d_mass_tab, \
-                       d_flags, d_res, d_poff, n_prot, n_res, d_tile_pf, d_blk, d_thr, d_out, d_ctr, d_hist)
-    if (!EMIT && !dp.semi && !dp.mand_mode && dp.cut_count) {
+#define DBI_DIGEST(SEMI, MAND)                                                                                   \
+    do {                                                                                                         \
+        if (dp.pf_kind)                                                                                          \
+            DBI_LAUNCH((k_digest<EMIT, SEMI, MAND, HIST, true>), dim3(nblk), dim3(DIGEST_THREADS), 0, s, dp,     \
+                       d_mass_tab, d_flags, d_res, d_poff, n_prot, n_res, d_tile_pf, d_blk, d_thr, d_out, d_ctr, \
+                       d_hist);                                                                                  \
+        else                                                                                                     \
+            DBI_LAUNCH((k_digest<EMIT, SEMI, MAND, HIST>), dim3(nblk), dim3(DIGEST_THREADS), 0, s, dp,           \
+                       d_mass_tab, d_flags, d_res, d_poff, n_prot, n_res, d_tile_pf, d_blk, d_thr, d_out, d_ctr, \
+                       d_hist);                                                                                  \
+    } while (0)
+    if (!EMIT && !dp.semi && !dp.mand_mode && dp.cut_count && !dp.pf_kind) {
         if (HIST && count_fast_ok(dp)) {
 #define DBI_COUNT_KT(KT)                                                                                   \
     DBI_LAUNCH((k_digest_count_cuts<HIST, true, KT>), dim3(nblk), dim3(DIGEST_THREADS), 0, s, dp, d_mass_tab, \
@@ -5181,6 +5297,7 @@ k_ptm_digest(DevParams dp, const double* __restrict__ mass_tab, const uint8_t* _
         uint32_t pep = 0;                  // pepSize
         uint32_t p = s;                    // next residue
         bool mand_all = false, mand_excl = false;  // mandatory residue in [s, p) / [s, p-1)
+        uint32_t focc = 0;                 // peptide filter, kind 1: counted residues in [s, p)
         while (m <= dp.max_mh) {           // :284 (end < length below)
             uint32_t q;                    // end: the peptide's last residue
             if (k < ee && ev_pos[k] == p) {  // '[' at end (:288-303)
@@ -5195,6 +5312,9 @@ k_ptm_digest(DevParams dp, const double* __restrict__ mass_tab, const uint8_t* _
                 q = p - 1;
             } else {
                 if (p >= Ls) break;
+                // the peptide filter sees the stripped residues [s, p] (:309-313; a formula step
+                // appends nothing to pepSeq and asks about the same string again: no new answer)
+                if (dp.pf_kind && filter_breaks(dp, flags_tab[T[p]], soff[i] + s, soff[i] + p, focc)) break;
                 ++pep;
                 m = m + mass_tab[T[p]];    // :306-308
                 q = p;

@@ -172,6 +172,13 @@ struct dbi_handle {
     // query scratch
     std::recursive_mutex qmu;           // query-side calls share scratch buffers and the stream
     DevBuf<double> win_lo, win_hi;      // dbi_set_windows: merged mass windows
+    // dbi_set_peptide_filter: the filter (kind 0: none), its hash (the persisted header's word),
+    // a motif's compiled form in HBM, and its match ends over the digest's residues / over the
+    // stripped PTM proteins (launch_filter_ends, before every digest)
+    dbi_peptide_filter pfilter{};
+    uint64_t pf_hash = 0;
+    DevBuf<dbi::PepFilterProg> pf_prog;
+    DevBuf<uint8_t> fend, fend_ptm;
     DevBuf<uint32_t> qdir;              // query directory (launch_qdir), rebuilt per index
     DevBuf<dbi::QueryDir> qdir_par;
     uint64_t build_serial = 0, qdir_serial = 0;
@@ -457,6 +464,9 @@ int read_counters(dbi_handle* h);
 const char* ptm_device_msg();  // ERR_PTM's message
 int begin_build(dbi_handle* h, uint64_t n_res, uint64_t n_prot, bool zero_ctr = true);  // zero_ctr false: the caller zeroes the counters on the stream itself
 int prepare_tiles(dbi_handle* h);
+// a motif peptide filter's match ends over h->d_res / h->d_poff (h->dp.fend), on the build
+// stream ahead of the digest that reads them; nothing for the other filters
+int prepare_filter(dbi_handle* h);
 // digest of h->d_res / h->d_poff into recA: *n records (*n_in slots, REC_SENTINEL
 // in the unused ones when *sparse)
 int run_digest(dbi_handle* h, uint64_t* n, uint64_t* n_in, bool* sparse, bool* dev_sized = nullptr);

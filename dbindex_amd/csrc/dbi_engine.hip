@@ -429,14 +429,27 @@ int prepare_tiles(dbi_handle* h) {
     return 0;
 }
 
+int prepare_filter(dbi_handle* h) {
+    if (h->dp.pf_kind != 2 || h->n_res == 0) return 0;
+    int rc;
+    if ((rc = h->fend.ensure(h->n_res + 16))) return rc;
+    h->dp.fend = h->fend.p;
+    STAGE(h, "filter_ends", by(2, 0, 0, 4, 0),
+          launch_filter_ends(h->pf_prog.p, h->d_res, h->d_poff, (uint32_t)h->n_prot, (uint32_t)h->n_res, h->fend.p,
+                             h->stream));
+    return 0;
+}
+
 // Warm builds digest into bounded slots: the lean kernel (full enzyme, no
 // mandatory residues, <= 2 missed cleavages) or the semi-specific one (no
-// mandatory residues); both without the unindexed search's windows.
+// mandatory residues); both without the unindexed search's windows and
+// without a peptide filter (its walks break per residue, like mandatory ones).
 bool lean_digest(const dbi_handle* h) {
-    return !h->dp.semi && !h->dp.mand_mode && h->dp.max_missed <= 2 && !h->dp.filter;
+    return !h->dp.semi && !h->dp.mand_mode && h->dp.max_missed <= 2 && !h->dp.filter && !h->dp.pf_kind;
 }
 bool bounded_digest(const dbi_handle* h) {
-    return lean_digest(h) || (h->dp.semi && !h->dp.mand_mode && !h->dp.filter && h->use_semi_bounded);
+    return lean_digest(h) ||
+           (h->dp.semi && !h->dp.mand_mode && !h->dp.filter && !h->dp.pf_kind && h->use_semi_bounded);
 }
 
 // Device digest over residues at d_res (n_res) with u32 offsets at h->d_poff.
@@ -451,7 +464,7 @@ int run_digest(dbi_handle* h, uint64_t* n_out, uint64_t* n_in_out, bool* sparse_
     if ((rc = h->blk.ensure(std::max<uint32_t>(nblk, 1))) || (rc = h->thr.ensure((size_t)nblk * DIGEST_THREADS + 1)))
         return rc;
     if ((rc = h->scan_tmp.ensure(std::max<size_t>(scan_u32_tmp_elems(nblk), h->scan_tmp.cap)))) return rc;
-    if ((rc = prepare_tiles(h))) return rc;
+    if ((rc = prepare_tiles(h)) || (rc = prepare_filter(h))) return rc;
     uint64_t n;
     // full enzyme, no mandatory residues, <= 2 missed cleavages: one walk into
     // per-tile reservations of exactly each start's candidate ends
@@ -1231,8 +1244,16 @@ int build_with_ptms(dbi_handle* h, const uint8_t* residues, uint64_t n_res, cons
     h->d_poff = o_off;
     h->n_res = n_res;
     if (rc) return rc;
+    // a motif filter's match ends over the stripped text the formula walks see
+    DevParams dpp = h->dp;
+    if (dpp.pf_kind == 2 && n_ptm) {
+        if ((rc = h->fend_ptm.ensure(sres.size() + 16))) return rc;
+        DBI_HIP(launch_filter_ends(h->pf_prog.p, h->ptm_res.p, h->ptm_soff.p, n_ptm, (uint32_t)sres.size(),
+                                   h->fend_ptm.p, s));
+        dpp.fend = h->fend_ptm.p;
+    }
     // the formula-carrying proteins: count, offsets, emit after the digest's slots
-    DBI_HIP(launch_ptm_digest(false, h->dp, h->mass_tab.p, h->flags_tab.p, h->ptm_res.p, h->ptm_soff.p, h->d_res,
+    DBI_HIP(launch_ptm_digest(false, dpp, h->mass_tab.p, h->flags_tab.p, h->ptm_res.p, h->ptm_soff.p, h->d_res,
                               h->d_poff, h->ptm_pid.p, h->ptm_evoff.p, h->ptm_evpos.p, h->ptm_evmass.p, n_ptm,
                               h->ptm_cnt.p, nullptr, h->ctr.p, s));
     DBI_HIP(launch_scan_u32(h->ptm_cnt.p, h->ptm_cnt.p, n_ptm, h->scan_tmp.p, h->scan_tmp.cap, h->ptm_total.p, s));
@@ -1249,7 +1270,7 @@ int build_with_ptms(dbi_handle* h, const uint8_t* residues, uint64_t n_res, cons
         std::swap(h->recA, grown);
         grown.release();
     }
-    DBI_HIP(launch_ptm_digest(true, h->dp, h->mass_tab.p, h->flags_tab.p, h->ptm_res.p, h->ptm_soff.p, h->d_res,
+    DBI_HIP(launch_ptm_digest(true, dpp, h->mass_tab.p, h->flags_tab.p, h->ptm_res.p, h->ptm_soff.p, h->d_res,
                               h->d_poff, h->ptm_pid.p, h->ptm_evoff.p, h->ptm_evpos.p, h->ptm_evmass.p, n_ptm,
                               h->ptm_cnt.p, h->recA.p + n_in, h->ctr.p, s));
     if ((rc = read_counters(h))) return rc;
@@ -1520,6 +1541,14 @@ void dbi_params_default(dbi_params* p, int32_t max_missed, int32_t semi) {
     p->index_factor = 8;
 }
 
+// residue class bits of the digest kernels; F_FOCC: the residue a max-occurrences filter counts
+static void class_flags(const dbi_params& p, const dbi_peptide_filter* f, uint8_t* fl) {
+    for (int c = 0; c < 256; ++c)
+        fl[c] = (p.cleave[c] ? F_CLEAVE : 0) | (p.nocut[c] ? F_NOCUT : 0) | (p.mandatory[c] ? F_MAND : 0) |
+                (c == '[' ? F_PTM : 0);
+    if (f && f->kind == 1) fl[(uint8_t)f->spec[0]] |= F_FOCC;
+}
+
 int dbi_open(const dbi_params* params, int device, dbi_handle** out) {
     if (!out) return set_error(DBI_E_INVALID, "out is NULL");
     *out = nullptr;
@@ -1545,9 +1574,7 @@ int dbi_open(const dbi_params* params, int device, dbi_handle** out) {
     if ((rc = h->mass_tab.ensure(256)) || (rc = h->flags_tab.ensure(256)) || (rc = h->ctr.ensure(1)))
         return fail(rc);
     uint8_t fl[256];
-    for (int c = 0; c < 256; ++c)
-        fl[c] = (params->cleave[c] ? F_CLEAVE : 0) | (params->nocut[c] ? F_NOCUT : 0) |
-                (params->mandatory[c] ? F_MAND : 0) | (c == '[' ? F_PTM : 0);
+    class_flags(*params, nullptr, fl);
     if (hipMemcpy(h->mass_tab.p, params->mass, sizeof(double) * 256, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->flags_tab.p, fl, 256, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(h->ctr.p, 0, sizeof(Counters)) != hipSuccess ||
@@ -1585,6 +1612,7 @@ void dbi_close(dbi_handle* h) {
     h->recR.release(); h->rdig.release(); h->rcur.release(); h->dsub.release(); h->dpre.release(); h->dmap.release();
     h->dheavy.release(); h->desc.release(); h->d1c.release(); h->hist2.release(); h->bstart.release();
     h->split_list.release();
+    h->pf_prog.release(); h->fend.release(); h->fend_ptm.release();
     drop_graph(h);
     for (auto& ev : h->evpool)
         if (ev) (void)hipEventDestroy(ev);
@@ -1974,7 +2002,7 @@ int dbi_set_windows(dbi_handle* h, const double* mass, const double* tol, uint64
         h->dp.n_win = 0;
         h->dp.win_max = INFINITY;
         h->dp.win_lo = h->dp.win_hi = nullptr;
-        h->dp.cut_count = make_dev_params(h->params).cut_count;
+        h->dp.cut_count = h->dp.pf_kind ? 0 : make_dev_params(h->params).cut_count;
         return 0;
     }
     // MassRangeFilteringIndex.init (:51-65): [m - tol, m + tol]; a NaN bound
@@ -2004,6 +2032,41 @@ int dbi_set_windows(dbi_handle* h, const double* mass, const double* tol, uint64
     h->dp.win_lo = h->win_lo.p;
     h->dp.win_hi = h->win_hi.p;
     h->dp.cut_count = 0;  // the stepping count does not see masses per peptide
+    return 0;
+}
+
+int dbi_set_peptide_filter(dbi_handle* h, const dbi_peptide_filter* f) {
+    if (!h) return set_error(DBI_E_INVALID, "NULL handle");
+    PepFilterProg prog;
+    int rc = pf_compile(f, &prog);  // a rejected pattern changes nothing
+    if (rc) return rc;
+    dbi_peptide_filter nf{};
+    if (f && f->kind == 1) {
+        nf.kind = 1;
+        nf.num_max = f->num_max;
+        nf.spec[0] = f->spec[0];
+    } else if (f && f->kind == 2) {
+        nf.kind = 2;
+        std::memcpy(nf.spec, f->spec, strnlen(f->spec, sizeof(f->spec) - 1));
+    }
+    DBI_HIP(hipSetDevice(h->device));
+    DBI_HIP(hipStreamSynchronize(h->stream));  // no digest in flight reads the tables written below
+    uint8_t fl[256];
+    class_flags(h->params, &nf, fl);
+    DBI_HIP(hipMemcpy(h->flags_tab.p, fl, 256, hipMemcpyHostToDevice));
+    if (nf.kind == 2) {
+        if ((rc = h->pf_prog.ensure(1))) return rc;
+        DBI_HIP(hipMemcpy(h->pf_prog.p, &prog, sizeof(prog), hipMemcpyHostToDevice));
+    }
+    h->pfilter = nf;
+    h->pf_hash = pf_hash(&nf);
+    h->dp.pf_kind = nf.kind;
+    h->dp.pf_max = nf.kind == 1 ? std::max(nf.num_max, 0) : 0;  // numMax < 0: the first one already exceeds it
+    h->dp.fend = nullptr;
+    // routed as mandatory residues are: exact walks, no cut-stepping count, no bounded digests
+    h->dp.cut_count = (nf.kind || h->dp.filter) ? 0 : make_dev_params(h->params).cut_count;
+    ++h->dp_gen;
+    h->built = false;  // an index built under another filter no longer answers
     return 0;
 }
 

@@ -105,6 +105,25 @@ constexpr uint8_t F_MAND = 4;
 constexpr uint8_t F_CUT = 8;    // window only: checkCleavage C-side ok at this residue (or protein end)
 constexpr uint8_t F_LAST = 16;  // window only: last residue of its protein
 constexpr uint8_t F_PTM = 32;   // '[': an inline formula (DBIndexer.java:288-303) where none may be
+constexpr uint8_t F_FOCC = 64;  // the counted residue of a max-occurrences peptide filter (dbi_set_peptide_filter)
+
+// Peptide filter (DBIndexer.java:309-313), compiled (dbi_filter.cpp).  A kind-2
+// pattern is n_alt alternatives of len[a] positions, each a 256-bit class
+// (bit c of mask[a][k]: byte c matches position k); the motif pre-pass
+// (launch_filter_ends) and dbi_peptide_filter_is_valid both read this form.
+constexpr int PF_MAX_ALTS = 8;
+constexpr int PF_MAX_ATOMS = 16;
+struct PepFilterProg {
+    uint32_t n_alt;
+    uint32_t len[PF_MAX_ALTS];
+    uint32_t mask[PF_MAX_ALTS][PF_MAX_ATOMS][8];
+};
+// validates f (NULL / kind 0: no filter) and compiles a kind-2 pattern; DBI_E_INVALID names the construct
+int pf_compile(const dbi_peptide_filter* f, PepFilterProg* prog);
+// isValid(seq) (PeptideFilterByMaxOccurrencies.java:21-32, PeptideFilterBySequence.java:22-29)
+bool pf_is_valid(const dbi_peptide_filter& f, const PepFilterProg& prog, const uint8_t* seq, uint64_t len);
+// FNV-1a 64 of (kind, num_max, spec); 0 for no filter, never 0 for one (the persisted header's word)
+uint64_t pf_hash(const dbi_peptide_filter* f);
 
 struct BinMap {
     double lo;
@@ -134,6 +153,13 @@ struct DevParams {
     double win_max;           // +inf without a filter
     const double* win_lo;     // device arrays, n_win each
     const double* win_hi;
+    // peptide filter (dbi_set_peptide_filter): a start's walk ends at the first
+    // end e whose peptide [s, e] is invalid, before anything else of that step
+    //   pf_kind 1: the (pf_max + 1)-th F_FOCC residue at or after s
+    //   pf_kind 2: fend[e] != 0 && fend[e] <= e - s + 1 (a motif match inside [s, e])
+    int32_t pf_kind;
+    int32_t pf_max;           // kind 1 (>= 0)
+    const uint8_t* fend;      // kind 2: launch_filter_ends over the residues being walked
 };
 
 // fine mass bins of a build: the one place the map's fields are computed
@@ -214,6 +240,12 @@ constexpr int BIG_CAP = 7936;       // records per oversize chunk sorted in LDS 
 
 // ---- launchers (dbi_device.hip) -------------------------------------------------
 // All return hipError_t of the launch.
+// Motif pre-pass of a kind-2 peptide filter: fend[e] = length of the shortest
+// alternative of *d_prog that matches ending at residue e without reaching
+// across the start of e's protein, 0 where none does (e < n_res).  Shortest =
+// latest match start, so "some match [b, e] has b >= s" is fend[e] <= e - s + 1.
+hipError_t launch_filter_ends(const PepFilterProg* d_prog, const uint8_t* d_res, const uint32_t* d_poff,
+                              uint32_t n_prot, uint32_t n_res, uint8_t* d_fend, hipStream_t s);
 // tile_pf[t] = protein holding residue min(t*DIGEST_TILE, R-1); ctr->max_plen
 // = longest protein (the record field width, see Rec)
 hipError_t launch_tile_proteins(const uint32_t* d_poff, uint32_t n_prot, uint32_t n_res, uint32_t* d_tile_pf,
@@ -355,7 +387,7 @@ hipError_t launch_ptm_digest(bool emit, const DevParams& dp, const double* d_mas
                              const uint8_t* d_sres, const uint32_t* d_soff, const uint8_t* d_ores,
                              const uint32_t* d_ooff, const uint32_t* d_pid, const uint32_t* d_ev_off,
                              const uint32_t* d_ev_pos, const double* d_ev_mass, uint32_t n_ptm, uint32_t* d_cnt,
-                             Rec* d_out, Counters* d_ctr, hipStream_t s);
+                             Rec* d_out, Counters* d_ctr, hipStream_t s);  // (dp.fend: over d_sres)
 
 // Owner map of a sharded build (dbi_shard_*): shard d owns the mass keys
 // (int)(m * factor) in [split[d-1], split[d]) (split[-1] = -inf, split[n-1] =
@@ -534,7 +566,7 @@ extern thread_local LaunchEvents t_launch_ev;
 int index_save(dbi_handle* h, const char* path, const std::string* defs, const std::vector<uint64_t>* def_off);
 int index_load(dbi_handle* h, const char* path, std::vector<uint8_t>* res_out, std::vector<uint64_t>* off_out,
                std::string* defs_out, std::vector<uint64_t>* def_off_out);
-int index_file_matches(const dbi_params& p, const char* path, bool* out);
+int index_file_matches(const dbi_params& p, const char* path, bool* out, uint64_t filter_hash = 0);
 
 // ---- error plumbing (dbi_engine.hip) ------------------------------------------------
 int set_error(int code, const std::string& msg);

@@ -40,7 +40,9 @@ struct dbi_index_header {
     uint32_t abi, reserved;
     uint64_t params_fp;
     uint64_t n_res, n_prot, n_unique, n_kept, n_total, n_dropped, n_keys, def_bytes;
-    uint64_t pad[5];
+    uint64_t filter_fp;  // pf_hash of the peptide filter the index was built under; 0: none (and every
+                         // file written before filters existed: this was a zero pad word)
+    uint64_t pad[4];
 };
 static_assert(sizeof(dbi_index_header) == 128, "128-B header");
 
@@ -116,6 +118,7 @@ int index_save(dbi_handle* h, const char* path, const std::string* defs, const s
     std::memcpy(hd.magic, MAGIC, 8);
     hd.abi = DBI_ABI_VERSION;
     hd.params_fp = params_fingerprint(h->params);
+    hd.filter_fp = h->pf_hash;
     hd.n_res = R;
     hd.n_prot = P;
     hd.n_unique = U;
@@ -152,6 +155,8 @@ int index_load(dbi_handle* h, const char* path, std::vector<uint8_t>* res_out, s
     if (rc) return rc;
     if (hd.params_fp != params_fingerprint(h->params))
         return io_fail("index file was built with other search parameters", path);
+    if (hd.filter_fp != h->pf_hash)  // ", pepFilter:" of the reference's params string (IndexUtil.java:295-296)
+        return io_fail("index file was built with another peptide filter", path);
     const uint64_t R = hd.n_res, P = hd.n_prot, U = hd.n_unique, K = hd.n_kept;
     if (R >= (1ull << 32) - 1 || P >= (1ull << 32) - 1 || K >= (1ull << 32) - 1)
         return io_fail("index file too large for one device", path);
@@ -248,14 +253,14 @@ int index_load(dbi_handle* h, const char* path, std::vector<uint8_t>* res_out, s
     return 0;
 }
 
-int index_file_matches(const dbi_params& p, const char* path, bool* out) {
+int index_file_matches(const dbi_params& p, const char* path, bool* out, uint64_t filter_hash) {
     *out = false;
     File f;
     f.f = std::fopen(path, "rb");
     if (!f.f) return 0;
     dbi_index_header hd;
     if (!get(f.f, &hd, 1) || std::memcmp(hd.magic, MAGIC, 8) != 0 || hd.abi != DBI_ABI_VERSION) return 0;
-    *out = hd.params_fp == params_fingerprint(p);
+    *out = hd.params_fp == params_fingerprint(p) && hd.filter_fp == filter_hash;
     return 0;
 }
 
@@ -277,6 +282,20 @@ int dbi_index_file_matches(const dbi_params* params, const char* path, int* out)
     if (!params || !path || !out) return set_error(DBI_E_INVALID, "NULL argument");
     bool m = false;
     const int rc = index_file_matches(*params, path, &m);
+    *out = m ? 1 : 0;
+    return rc;
+}
+
+int dbi_index_file_matches_filtered(const dbi_params* params, const dbi_peptide_filter* f, const char* path,
+                                    int* out) {
+    if (!params || !path || !out) return set_error(DBI_E_INVALID, "NULL argument");
+    PepFilterProg prog;
+    int rc = pf_compile(f, &prog);  // an invalid filter matches nothing: say so
+    if (rc) return rc;
+    dbi_peptide_filter nf{};  // hashed as dbi_set_peptide_filter stores it
+    if (f && f->kind) nf = *f;
+    bool m = false;
+    rc = index_file_matches(*params, path, &m, pf_hash(&nf));
     *out = m ? 1 : 0;
     return rc;
 }

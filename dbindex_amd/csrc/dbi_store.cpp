@@ -38,6 +38,7 @@ struct dbi_store {
     dbi_handle* eng = nullptr;
     bool inited = false, in_tx = false, device_digest = false, persist = false;
     int unindexed = 0;          // MassRangeFilteringIndex mode (SEARCH_UNINDEXED): 0 off, 1 resident, 2 stream
+    dbi_peptide_filter pf{};    // sparam.getPeptideFilter() (kind 0: null): the engine's filter and the index file's
     uint64_t last_matches = 0;  // unindexed: size of the last cutAndSearch result
     std::mutex search_mu;       // STREAM searches rebuild the engine's index: one at a time
     std::string db_id;
@@ -160,6 +161,7 @@ int ensure_engine(dbi_store* s) {
     if (s->eng) return 0;
     int rc = dbi_open(&s->p, s->device, &s->eng);
     if (!rc && s->unindexed) rc = dbi_set_bucket_drop(s->eng, 0);
+    if (!rc && s->pf.kind) rc = dbi_set_peptide_filter(s->eng, &s->pf);
     return rc;
 }
 
@@ -222,6 +224,17 @@ int dbi_store_set_unindexed(dbi_store* s, int on) {
     return 0;
 }
 
+int dbi_store_set_peptide_filter(dbi_store* s, const dbi_peptide_filter* f) {
+    if (!s) return set_error(DBI_E_INVALID, "NULL store");
+    if (s->inited) return set_error(DBI_E_STATE, "set the peptide filter before init()");
+    PepFilterProg prog;
+    const int rc = pf_compile(f, &prog);  // a rejected pattern is an error here, not at the first build
+    if (rc) return rc;
+    s->pf = dbi_peptide_filter{};
+    if (f && f->kind) s->pf = *f;
+    return 0;
+}
+
 int dbi_store_init(dbi_store* s, const char* database_id) {
     if (!s) return set_error(DBI_E_INVALID, "NULL store");
     if (!database_id || !*database_id)
@@ -232,7 +245,7 @@ int dbi_store_init(dbi_store* s, const char* database_id) {
         // an index of these parameters on disk: load it (DBIndexStoreSQLiteMult.init :92-149)
         const std::string path = s->db_id + ".dbihip";
         bool match = false;
-        int rc = index_file_matches(s->p, path.c_str(), &match);
+        int rc = index_file_matches(s->p, path.c_str(), &match, pf_hash(&s->pf));
         if (rc) return rc;
         if (match) {
             if ((rc = ensure_engine(s))) return rc;

@@ -138,7 +138,7 @@ int count_impl(dbi_handle* h, const uint8_t* d_res, uint64_t n_res, const uint64
     h->d_res = d_res;
     h->d_poff = h->poff.p;
     if (n_res) {
-        if ((rc = prepare_tiles(h))) return rc;
+        if ((rc = prepare_tiles(h)) || (rc = prepare_filter(h))) return rc;
         if (d_hist)
             STAGE(h, "digest_count", by(1, 0, 0, 4, 0),
                   launch_digest_count_hist(h->dp, h->mass_tab.p, h->flags_tab.p, h->d_res, h->d_poff,

@@ -16,7 +16,7 @@ import numpy as np
 from . import _native
 from ._native import DbiDeviceHits, DbiDeviceIndex, DbiQueryResult, DbiStats, check
 from .fasta import PackedProteins
-from .params import DBIndexSearchParams, DbiParams
+from .params import DBIndexSearchParams, DbiParams, peptide_filter_to_c
 
 
 def _p(a: np.ndarray):
@@ -40,10 +40,14 @@ class BuildStats:
 
 
 class Engine:
-    def __init__(self, params, device: int = 0, options=None):
+    def __init__(self, params, device: int = 0, options=None, peptide_filter=None):
         """options: {name: value} for dbi_set_option / dbi_set_option_str
-        (tuning switches and test hooks, e.g. {"depth_bins": 0})."""
+        (tuning switches and test hooks, e.g. {"depth_bins": 0}).
+        peptide_filter: sparam.getPeptideFilter() (default: the one of a
+        DBIndexSearchParams given as params)."""
         if isinstance(params, DBIndexSearchParams):
+            if peptide_filter is None:
+                peptide_filter = params.peptide_filter
             params = params.to_c()
         assert isinstance(params, DbiParams)
         self.cparams = params
@@ -54,6 +58,8 @@ class Engine:
         self._keep = None
         for k, v in (options or {}).items():
             self.set_option(k, v)
+        if peptide_filter is not None:
+            self.set_peptide_filter(peptide_filter)
 
     def set_option(self, name: str, value) -> None:
         """dbi_set_option (int) or dbi_set_option_str (str)."""
@@ -272,6 +278,12 @@ class Engine:
         t = np.ascontiguousarray(tol if tol is not None else [], np.float64)
         check(_native.lib().dbi_set_windows(self.h, m.ctypes.data_as(ctypes.c_void_p),
                                             t.ctypes.data_as(ctypes.c_void_p), m.shape[0], 1 if on else 0))
+
+    def set_peptide_filter(self, f=None) -> None:
+        """``dbi_set_peptide_filter``: the next builds and counts leave a start's
+        walk at its first invalid peptide (None removes the filter)."""
+        c = peptide_filter_to_c(f)
+        check(_native.lib().dbi_set_peptide_filter(self.h, ctypes.byref(c) if c is not None else None))
 
     def rebuild(self) -> BuildStats:
         """``dbi_rebuild``: build again over the resident inputs of the last build."""

@@ -48,6 +48,8 @@ class DBIndexer:
         if mode == IndexerMode.SEARCH_UNINDEXED and not isinstance(indexStore, MassRangeFilteringIndexHip):
             raise DBIndexerException("SEARCH_UNINDEXED needs the MassRangeFilteringIndex store")
         self.indexStore = indexStore
+        if sparam.peptide_filter is not None:  # peptideFilter = sparam.getPeptideFilter() (:148, :171)
+            self.indexStore.setPeptideFilter(sparam.peptide_filter)
         self.indexStore.setDeviceDigest(True)
         self.protNum = -1
         self.decoyDiscarded = 0

@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass, field
-from typing import Dict, Optional
+from typing import Dict, Optional, Union
 
 # Pinned monoisotopic residue masses (Da).  Letters absent here map to 0.0.
 MONO_RESIDUE_MASS: Dict[str, float] = {
@@ -68,6 +68,83 @@ class DbiParams(ctypes.Structure):
     ]
 
 
+class DbiPeptideFilter(ctypes.Structure):
+    """ctypes image of ``struct dbi_peptide_filter`` (include/dbindex_hip.h)."""
+
+    _fields_ = [("kind", ctypes.c_int32), ("num_max", ctypes.c_int32), ("spec", ctypes.c_char * 120)]
+
+
+def _checked_filter(c: DbiPeptideFilter) -> DbiPeptideFilter:
+    """The native compile of the filter; its error as ``ValueError``."""
+    from . import _native  # (late: _native imports this module)
+    v = ctypes.c_int()
+    if _native.lib().dbi_peptide_filter_is_valid(ctypes.byref(c), b"", 0, ctypes.byref(v)) != 0:
+        raise ValueError(_native.last_error())
+    return c
+
+
+@dataclass(frozen=True)
+class PeptideFilterByMaxOccurrences:
+    """``util/PeptideFilterByMaxOccurrencies.java``: a peptide holding ``aa``
+    more than ``num_max`` times is discarded (``DigestionConfiguration`` builds
+    it from a string such as ``"C2"``)."""
+
+    aa: str
+    num_max: int
+
+    def __post_init__(self):
+        if not self.aa:
+            raise ValueError("aa must hold a residue")
+        object.__setattr__(self, "aa", self.aa[0])  # aa.toCharArray()[0]
+
+    def is_valid(self, seq: str) -> bool:
+        return seq.count(self.aa) <= max(int(self.num_max), 0)
+
+    def __str__(self) -> str:
+        return f"{self.aa}{int(self.num_max)}"  # String.valueOf(aa) + numMaxOccurrencies
+
+    def to_c(self) -> DbiPeptideFilter:
+        c = DbiPeptideFilter(kind=1, num_max=int(self.num_max))
+        c.spec = self.aa.encode("latin-1")
+        return _checked_filter(c)
+
+
+@dataclass(frozen=True)
+class PeptideFilterBySequence:
+    """``util/PeptideFilterBySequence.java``: a peptide in which ``regexp`` is
+    found (``Matcher.find``) is discarded.  The engine accepts the patterns
+    that are plain motif searches (include/dbindex_hip.h); ``to_c`` raises
+    ``ValueError`` for any other."""
+
+    regexp: str
+
+    def is_valid(self, seq: str) -> bool:
+        from . import _native
+        c = self.to_c()
+        b = seq.encode("latin-1")
+        v = ctypes.c_int()
+        _native.check(_native.lib().dbi_peptide_filter_is_valid(ctypes.byref(c), b, len(b), ctypes.byref(v)))
+        return bool(v.value)
+
+    def __str__(self) -> str:
+        return self.regexp  # pattern.pattern()
+
+    def to_c(self) -> DbiPeptideFilter:
+        b = self.regexp.encode("latin-1")
+        if len(b) > 119:
+            raise ValueError("peptide filter pattern: more than 119 characters")
+        c = DbiPeptideFilter(kind=2, num_max=0)
+        c.spec = b
+        return _checked_filter(c)
+
+
+def peptide_filter_to_c(f) -> Optional[DbiPeptideFilter]:
+    """``None`` / a filter object / a ``DbiPeptideFilter`` -> the C struct (or None)."""
+    if f is None or isinstance(f, DbiPeptideFilter):
+        return f
+    return f.to_c()
+
+
 @dataclass
 class DBIndexSearchParams:
     """Mirror of the getters ``DBIndexer.cutSeq`` and the SQLiteMult store read.
@@ -90,6 +167,9 @@ class DBIndexSearchParams:
     index_factor: int = 8
     mandatory_internal_aas: Optional[str] = None
     discard_decoy_regexp: Optional[str] = None  # getDiscardDecoyRegexp (DBIndexSearchParamsImpl.java:483)
+    # getPeptideFilter (DBIndexSearchParamsImpl.java:444): not part of dbi_params / to_c();
+    # the engine, the stores and the sharded build hand it to dbi_set_peptide_filter
+    peptide_filter: "Optional[Union[PeptideFilterByMaxOccurrences, PeptideFilterBySequence]]" = None
     min_pep_length: int = MIN_PEP_LENGTH
     h2o_proton: float = H2O_PROTON
     cterm: float = 0.0

@@ -163,9 +163,16 @@ class ShardComm:
             pass
 
 
+KEEP_FILTER = object()  # peptide_filter default: the engines keep the filter they have
+
+
 def build_sharded(eng: Engine, comm: ShardComm, d_res: int, n_res: int, d_off: int, n_prot: int,
-                  p_begin: int, p_end: int) -> DbiShardStats:
-    """All phases over RCCL (dbi_build_sharded): this rank's owner slice."""
+                  p_begin: int, p_end: int, peptide_filter=KEEP_FILTER) -> DbiShardStats:
+    """All phases over RCCL (dbi_build_sharded): this rank's owner slice.
+    ``peptide_filter``: set on the engine first (every rank must pass the same:
+    each shard's digest applies its own handle's filter)."""
+    if peptide_filter is not KEEP_FILTER:
+        eng.set_peptide_filter(peptide_filter)
     check(_native.lib().dbi_build_sharded(eng.h, comm.h, ctypes.c_void_p(d_res), n_res, ctypes.c_void_p(d_off),
                                           n_prot, p_begin, p_end))
     return shard_stats(eng)
@@ -173,14 +180,18 @@ def build_sharded(eng: Engine, comm: ShardComm, d_res: int, n_res: int, d_off: i
 
 def build_sharded_local(engines: Sequence[Engine], d_res: int, n_res: int, d_off: int, n_prot: int,
                         ranges: Sequence[Tuple[int, int]], profile=None, balance: bool = False,
-                        split: Optional[np.ndarray] = None) -> np.ndarray:
+                        split: Optional[np.ndarray] = None, peptide_filter=KEEP_FILTER) -> np.ndarray:
     """Every shard's handle in this process (exchange by device copies): the
     phases of dbi_build_sharded one by one.  ``profile`` = (band_split,
     band_cost): cost-balanced splitters; ``balance``: the splitters follow the
     merge-cost profile engines[0] keeps and this build updates, as
     dbi_build_sharded does; ``split``: these owner splitters (a warm
-    dbi_build_sharded reusing its split).  Returns the owner splitters."""
+    dbi_build_sharded reusing its split); ``peptide_filter``: set on every
+    shard's engine first (None removes it).  Returns the owner splitters."""
     n = len(engines)
+    if peptide_filter is not KEEP_FILTER:
+        for eng in engines:
+            eng.set_peptide_filter(peptide_filter)
     assert 1 <= n <= MAX_SHARDS and len(ranges) == n
     L = _native.lib()
     samples = np.zeros((n, SHARD_SAMPLES + 1), np.float64)

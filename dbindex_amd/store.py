@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _native
 from ._native import DbiSeqList, DBIndexStoreException, check
-from .params import DBIndexSearchParams, DbiParams
+from .params import DBIndexSearchParams, DbiParams, peptide_filter_to_c
 
 FilterResult_INCLUDE = _native.FILTER_INCLUDE
 FilterResult_SKIP = _native.FILTER_SKIP
@@ -179,6 +179,8 @@ class DBIndexStoreHip:
         s = ctypes.c_void_p()
         check(_native.lib().dbi_store_create(ctypes.byref(cp), device, ctypes.byref(s)))
         self.s = s
+        if self.sparam is not None and self.sparam.peptide_filter is not None:
+            self.setPeptideFilter(self.sparam.peptide_filter)
         if device_digest:
             self.setDeviceDigest(True)
         if persist:  # <databaseID>.dbihip: loaded by init() when it matches, written by stopAddSeq()
@@ -198,6 +200,12 @@ class DBIndexStoreHip:
     # --- DBIndexerHip hook ----------------------------------------------------
     def setDeviceDigest(self, on: bool) -> None:
         check(_native.lib().dbi_store_set_device_digest(self.s, 1 if on else 0))
+
+    def setPeptideFilter(self, f) -> None:
+        """sparam.getPeptideFilter() (before init): applied by the device digest,
+        and part of the persisted index's identity (``dbi_store_set_peptide_filter``)."""
+        c = peptide_filter_to_c(f)
+        check(_native.lib().dbi_store_set_peptide_filter(self.s, ctypes.byref(c) if c is not None else None))
 
     # --- DBIndexStore ---------------------------------------------------------
     def lastBuffertoDatabase(self) -> None:

@@ -126,7 +126,9 @@ int dbi_build_device(dbi_handle* h, const uint8_t* d_residues, uint64_t n_res,
 /* Build from externally supplied occurrences (DBIndexStore.addSequence path):
  * mass / protein id / offset-in-protein / length per occurrence, in insertion
  * order, over the protein residues given as above.  Dedup + sort + query are
- * identical to the device-digest build. */
+ * identical to the device-digest build.  A peptide filter of the handle
+ * (dbi_set_peptide_filter) is not applied: the caller's cutSeq already did
+ * (DBIndexer.java:309-313). */
 int dbi_build_occurrences(dbi_handle* h, const uint8_t* residues, uint64_t n_res,
                           const uint64_t* prot_off, uint64_t n_prot,
                           const double* mass, const uint32_t* prot_id,
@@ -153,8 +155,40 @@ int dbi_set_bucket_drop(dbi_handle* h, int on);
 int dbi_set_windows(dbi_handle* h, const double* mass, const double* tol, uint64_t n, int on);
 
 /* Build again over the inputs of the last dbi_build (still resident in HBM),
- * under the current windows / bucket setting. */
+ * under the current windows / bucket / peptide-filter setting. */
 int dbi_rebuild(dbi_handle* h);
+
+/* sparam.getPeptideFilter() (DBIndexer.java:148,171): cutSeq appends a residue
+ * to the peptide, asks isValid(peptide) and leaves the start's walk when the
+ * answer is false, before the cleavage test and any emit (:305-313).
+ *   kind 1  PeptideFilterByMaxOccurrencies(aa, numMax) (util/
+ *           PeptideFilterByMaxOccurrencies.java:21-32): invalid once the
+ *           peptide holds spec[0] more than num_max times (num_max < 0 acts
+ *           as 0); DigestionConfiguration.getPeptideFilter builds it from
+ *           a string such as "C2".
+ *   kind 2  PeptideFilterBySequence(regexp) (util/PeptideFilterBySequence.java:
+ *           18-29): invalid once the pattern is found in the peptide.  The
+ *           accepted patterns are those where Matcher.find is a plain motif
+ *           search: alt ('|' alt)*, at most 8 alternatives of 1..16 atoms, an
+ *           atom a literal byte, '.', or a class [...] / [^...] of bytes and
+ *           a-b ranges.  Quantifiers, groups, anchors, escapes, an empty
+ *           alternative or more than 119 characters are DBI_E_INVALID (the
+ *           message names the construct), never ignored. */
+typedef struct dbi_peptide_filter {
+    int32_t kind;      /* 0 none, 1 max occurrences, 2 sequence motif */
+    int32_t num_max;   /* kind 1 */
+    char spec[120];    /* kind 1: spec[0] = the residue; kind 2: NUL-terminated pattern */
+} dbi_peptide_filter;
+/* The filter of the next builds and counts (dbi_build, dbi_build_device,
+ * dbi_rebuild, dbi_count, dbi_count_buckets, the PTM build, dbi_shard_digest
+ * and the sharded builds); NULL or kind 0 removes it.  Part of the index's
+ * identity (IndexUtil.java:295-296): clears the built index, like
+ * dbi_set_windows.  dbi_build_occurrences does not apply it: those
+ * occurrences come from a cutSeq that already asked the filter. */
+int dbi_set_peptide_filter(dbi_handle* h, const dbi_peptide_filter* f);
+/* isValid(seq) of the filter (the same compiled matcher the device uses);
+ * host only.  *out = 1 valid, 0 invalid. */
+int dbi_peptide_filter_is_valid(const dbi_peptide_filter* f, const char* seq, uint64_t len, int* out);
 
 /* Threading: a build (dbi_build*, dbi_rebuild, dbi_count,
  * dbi_index_load, the dbi_shard_* phases) is exclusive per handle.  Query-side
@@ -487,6 +521,13 @@ int dbi_index_save(dbi_handle* h, const char* path);
 int dbi_index_load(dbi_handle* h, const char* path);  /* replaces the handle's index */
 /* *out = 1 when `path` holds an index built with exactly these parameters (host only) */
 int dbi_index_file_matches(const dbi_params* params, const char* path, int* out);
+/* The same for an index built under a peptide filter (", pepFilter:" in the
+ * params string the reference hashes, IndexUtil.java:295-296): the header
+ * carries a hash of (kind, num_max, spec), 0 without a filter, and a handle
+ * loads a file only under the filter it was saved with.  f NULL or kind 0:
+ * dbi_index_file_matches (a filtered file does not match plain params). */
+int dbi_index_file_matches_filtered(const dbi_params* params, const dbi_peptide_filter* f, const char* path,
+                                    int* out);
 
 /* ------------------------------------------------------------------------ */
 /* DBIndexStore mirror                                                      */
@@ -520,6 +561,12 @@ int dbi_store_set_persist(dbi_store* s, int on);
  * getEntryKeys() is not supported.  Needs non-negative residue masses and a
  * max precursor mass < 65536 Da. */
 int dbi_store_set_unindexed(dbi_store* s, int mode);
+/* sparam.getPeptideFilter() of the store's DBIndexer (before init; NULL or
+ * kind 0 removes): the device digest (stopAddSeq with device digestion, both
+ * unindexed modes) applies it, and the persisted index is found and written
+ * under it (indexExists, IndexUtil.java:295-296).  Occurrences passed to
+ * addSequence are taken as given. */
+int dbi_store_set_peptide_filter(dbi_store* s, const dbi_peptide_filter* f);
 #define DBI_UNINDEXED_RESIDENT 1 /* one device index of every peptide; searches are windows over it  */
 #define DBI_UNINDEXED_STREAM   2 /* proteins resident; every search re-digests them through its       */
                                  /* ranges (dbi_set_windows): memory for the matches only, for        */

@@ -223,6 +223,26 @@ JNIEXPORT void JNICALL JFN(setUnindexed0)(JNIEnv* e, jclass k, jlong h, jint mod
     fail(e, dbi_store_set_unindexed(STORE(h), mode));
 }
 
+/* sparam.getPeptideFilter() (DBIndexer.java:148,171) as (kind, numMax, spec):
+ * 0 none; 1 PeptideFilterByMaxOccurrencies (spec = the residue); 2
+ * PeptideFilterBySequence (spec = pattern.pattern()).  The shim's side of the
+ * binding only: DBIndexStoreHip declares no native for it yet. */
+JNIEXPORT void JNICALL JFN(setPeptideFilter0)(JNIEnv* e, jclass k, jlong h, jint kind, jint numMax, jstring spec) {
+    (void)k;
+    dbi_peptide_filter f;
+    memset(&f, 0, sizeof f);
+    f.kind = kind;
+    f.num_max = numMax;
+    if (spec) {
+        const char* c = (*e)->GetStringUTFChars(e, spec, NULL);
+        if (!c) return;  /* OutOfMemoryError pending */
+        /* a longer pattern fills spec without a NUL: rejected by name, not cut short */
+        for (size_t i = 0; i < sizeof f.spec && c[i]; ++i) f.spec[i] = c[i];
+        (*e)->ReleaseStringUTFChars(e, spec, c);
+    }
+    fail(e, dbi_store_set_peptide_filter(STORE(h), &f));
+}
+
 /* dbi_seq_list -> DBIndexStoreHip.SeqList (flat arrays; Java builds the
  * IndexedSequence objects, DBIndexStoreHip.toList) */
 static int set_array(JNIEnv* e, jobject o, jclass c, const char* name, const char* sig, jobject arr) {
